@@ -1,7 +1,6 @@
 """CPU: the oracle's per-read chain (event detection -> scalings -> ABEA -> recalibration) against the
 reference's goldens for test/ecoli_2kb_region (adaptive.exp, est_scalings.exp, recalib_scalings.exp)."""
 import os
-import sys
 import numpy as np
 import pytest
 
@@ -40,17 +39,9 @@ def test_real_signal_chain_matches_reference_goldens(orc, r9):
     assert n == 10
 
 
-@pytest.mark.skipif(not (os.path.exists("/root/reference/test/ecoli_2kb_region/fast5_files")
-                         and os.path.exists("/opt/conda/bin/h5dump")), reason="needs the reference data + h5dump")
-def test_all_112_ecoli_reads_against_goldens():
-    """Build container only: every FAST5 of the reference's test set through the oracle chain; all 111 unique
-    adaptive.exp records are reproduced (the 112th read is not in the BAM)."""
-    sys.path.insert(0, GOLD)
-    import make_ecoli_golden as M
-    r = M.main(write=False)
-    assert r["n"] == 112 and r["gold_unique"] == 111
-    assert r["covered"] == 111 and r["adaptive"] == 111
-    assert r["est"] >= 111 and r["recalib"] >= 110
+# Every FAST5 of the test set (112 reads, 5.5 M raw samples: more than a fixture here should hold) through the same chain is
+# tests/golden/make_ecoli_golden.py --check, run where the f5c test data is; the committed fixtures cover 10 reads from the raw
+# signal (above) and all 111 reads of the BAM from their event tables (test_all_111_reads_mean_only_events_against_printed_goldens below).
 
 
 @pytest.mark.gpu

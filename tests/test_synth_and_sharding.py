@@ -108,3 +108,41 @@ def test_lpt_split_of_the_100k_batch_over_8_gpus_is_balanced():
         pre = synth.lpt_bins(3 * g["read_len"].astype(np.int64), bins)
         load = np.bincount(pre, weights=w, minlength=bins)
         assert (np.abs(load / load.mean() - 1.0) < 0.02).all(), load / load.mean()
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(r9, tmp_path):
+    """bench.py --dump-outputs: the sample of reads whose pair lists are written depends on the inputs only (the same reads
+    whatever the build returns), the files stay inside the byte budget, and the arrays hold exactly what the caller's buffers
+    held: n_pairs of every read, and each sampled read's first n_pairs pairs, in read order."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from f5c_amd import synth
+    from f5c_amd.types import PAIR_DT
+    k, model = r9
+    batch = synth.make_batch(120, model, k, seed=20250003, law="loguniform", chunk_reads=32, workers=2)
+    cap = batch["n_events"].astype(np.int64) + batch["read_len"]
+    budget = 2 << 20
+    samples = []
+    for seed in (1, 2):                                       # two "builds" returning different pair lists
+        rng = np.random.default_rng(seed)
+        view = {"n_pairs": (rng.random(len(cap)) * cap).astype(np.int32), "pairs": np.zeros(batch["pair_cap"], PAIR_DT)}
+        view["pairs"]["ref_pos"] = rng.integers(0, 1 << 20, batch["pair_cap"])
+        view["pairs"]["read_pos"] = rng.integers(0, 1 << 20, batch["pair_cap"])
+        ptr = batch["pair_ptr"]
+        a = bench.output_sample(view["n_pairs"], batch, lambda i, m: view["pairs"][ptr[i]:ptr[i] + m], budget=budget)
+        flat = view["pairs"].view(np.int32)                   # the device batch's layout: int32 [2 x pair_cap]
+        b = bench.output_sample(view["n_pairs"], batch, lambda i, m: flat[2 * ptr[i]:][:2 * m].view(PAIR_DT), budget=budget)
+        assert all((a[k_] == b[k_]).all() for k_ in a)
+        assert sum(x.nbytes for x in a.values()) <= budget
+        assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+        assert (a["n_pairs"] == view["n_pairs"]).all()
+        reads = a["sample_reads"].astype(np.int64)
+        assert 0 < len(reads) < len(cap) and (np.diff(reads) > 0).all()
+        want = np.concatenate([view["pairs"][batch["pair_ptr"][i]:batch["pair_ptr"][i] + view["n_pairs"][i]] for i in reads])
+        assert (a["sample_pairs"][:, 0] == want["ref_pos"]).all() and (a["sample_pairs"][:, 1] == want["read_pos"]).all()
+        samples.append(reads)
+    assert (samples[0] == samples[1]).all()
+    line = bench.write_outputs(str(tmp_path / "out"), a)
+    for name in ("n_pairs", "sample_reads", "sample_pairs"):
+        assert (np.load(tmp_path / "out" / f"{name}.npy") == a[name]).all()
+    assert line["bytes"] == sum(x.nbytes for x in a.values())
