@@ -18,9 +18,16 @@ EXPORTS = ["abea_init", "abea_init_multi", "abea_device_count", "abea_free", "ab
            "abea_device_info", "abea_selftest", "abea_rsq_format", "abea_lpt_split", "abea_hmm_score_batch_host", "abea_expand_walk_codes", "abea_expand_walk_codes_to_map",
            "abea_host_plan_chunks", "abea_host_plan_threads", "abea_set_inflight", "abea_align_batch_host_submit",
            "abea_align_batch_host_wait", "abea_events_batch_host", "abea_process_batch_host", "abea_rsq_format_batch",
-           "abea_hmm_score_batch_device", "abea_expand_kmer_counts_to_map", "abea_flatten_event_means", "abea_link_probe"]
+           "abea_hmm_score_batch_device", "abea_expand_kmer_counts_to_map", "abea_flatten_event_means", "abea_link_probe",
+           "abea_events_batch_host_fields", "abea_process_batch_host_fields"]
 SHIM_EXPORTS = ["abea_f5c_init", "abea_f5c_align", "abea_f5c_align_scale", "abea_f5c_free", "abea_f5c_align_submit",
-                "abea_f5c_align_wait", "abea_f5c_event_db", "abea_f5c_process"]      # include/abea_f5c_shim.h
+                "abea_f5c_align_wait", "abea_f5c_event_db", "abea_f5c_process", "abea_f5c_event_db_fields",
+                "abea_f5c_process_fields"]      # include/abea_f5c_shim.h
+
+# which event-table fields the raw-signal entries hand back (ABEA_EV_FIELDS_*, include/abea.h); unselected fields come back as +0.0f
+EV_FIELDS_ALL = 0        # start, length, mean, stdv (eventalign)
+EV_FIELDS_NO_STDV = 1    # start, length, mean (call-methylation)
+EV_FIELDS_LAYOUT = 2     # start, length (resquiggle)
 
 
 class AbeaError(RuntimeError):
@@ -422,18 +429,20 @@ class AbeaContext:
                                     _p(v["read_stat_flag"]), _p(v["n_event_alignment"]), 0, 0)
         return v
 
-    def events_view(self, view):
-        """abea_events_batch_host = event_db (f5c.c:682-734) on the view's signals."""
-        self._lib.abea_events_batch_host.restype = C.c_int
-        self._lib.abea_events_batch_host.argtypes = [C.c_void_p, C.POINTER(_EventsHostBatch)]
-        self._chk(self._lib.abea_events_batch_host(self._h, C.byref(view["eb"])), "abea_events_batch_host")
+    def events_view(self, view, ev_fields=EV_FIELDS_ALL):
+        """abea_events_batch_host_fields = event_db (f5c.c:682-734) on the view's signals; `ev_fields` (EV_FIELDS_*) selects
+        the fields of the tables that come back, the others are +0.0f."""
+        self._lib.abea_events_batch_host_fields.restype = C.c_int
+        self._lib.abea_events_batch_host_fields.argtypes = [C.c_void_p, C.POINTER(_EventsHostBatch), C.c_uint32]
+        self._chk(self._lib.abea_events_batch_host_fields(self._h, C.byref(view["eb"]), ev_fields), "abea_events_batch_host_fields")
 
-    def process_view(self, view):
-        """abea_process_batch_host = event_db -> align_db -> scaling_db (resquiggle.c:283-315) on the view's signals."""
-        self._lib.abea_process_batch_host.restype = C.c_int
-        self._lib.abea_process_batch_host.argtypes = [C.c_void_p, C.POINTER(_ProcessBatch)]
+    def process_view(self, view, ev_fields=EV_FIELDS_ALL):
+        """abea_process_batch_host_fields = event_db -> align_db -> scaling_db (resquiggle.c:283-315) on the view's signals;
+        `ev_fields` selects the fields of the returned tables and changes no other output."""
+        self._lib.abea_process_batch_host_fields.restype = C.c_int
+        self._lib.abea_process_batch_host_fields.argtypes = [C.c_void_p, C.POINTER(_ProcessBatch), C.c_uint32]
         view["read_stat_flag"][:] = 0
-        self._chk(self._lib.abea_process_batch_host(self._h, C.byref(view["pb"])), "abea_process_batch_host")
+        self._chk(self._lib.abea_process_batch_host_fields(self._h, C.byref(view["pb"]), ev_fields), "abea_process_batch_host_fields")
 
     @staticmethod
     def view_events(view, i):

@@ -34,6 +34,8 @@
 extern "C" __global__ void abea_ev_compact_kernel(int, const abea_event_t*, const int64_t*, const int64_t*, const int32_t*,
                                                   abea_event_t*);
 extern "C" __global__ void abea_ev_pack_kernel(int, const abea_event_t*, const int64_t*, const int64_t*, const int32_t*, uint4*);
+extern "C" __global__ void abea_ev_pack8_kernel(int, const abea_event_t*, const int64_t*, const int64_t*, const int32_t*, uint4*);   /* abea_evpack.hip */
+extern "C" __global__ void abea_ev_pack4_kernel(int, const abea_event_t*, const int64_t*, const int64_t*, const int32_t*, uint4*);
 
 namespace {
 
@@ -52,6 +54,7 @@ struct abea_chain_slot {
     hipEvent_t e_cnt = nullptr, e_done = nullptr, t0 = nullptr, t1 = nullptr, t2 = nullptr, t3 = nullptr, t4 = nullptr;
     hipEvent_t e_cmp = nullptr, e_tab = nullptr;     /* compaction done (kernel stream) / tables down (dstream) */
     bool tab_on_dstream = false, packed = false;
+    int rec_words = 3;                               /* 32-bit words per table record over PCIe: 6 = event_t, 3 / 2 / 1 = packed */
     pinned_buf up, cnt, desc, dn, tab;
     void* idx_p = nullptr; size_t idx_cap = 0;       /* grown by abea_detect_events_on */
     bool busy = false, staged = false;
@@ -117,6 +120,15 @@ chain_opts read_chain_opts() {
     if (const char* e = getenv("ABEA_CHAIN_TABLE_COPY")) o.copy_engine = strcmp(e, "engine") == 0;
     o.reads_max = std::max(o.reads_max, o.reads_min);
     return o;
+}
+
+/* 32-bit words per event of the table records that cross PCIe for a field selection (include/abea.h): ABEA_EV_FIELDS_ALL keeps the
+ * A/B knob above (12-byte {start, mean, stdv} records, or whole 24-byte event_t with ABEA_CHAIN_TABLE_FORMAT=full); the narrower
+ * selections always use their own records, {start, mean} and {start} (abea_evpack.hip) */
+int chain_rec_words(const chain_opts& o, uint32_t ev_fields) {
+    if (ev_fields == ABEA_EV_FIELDS_LAYOUT) return 1;
+    if (ev_fields == ABEA_EV_FIELDS_NO_STDV) return 2;
+    return o.packed ? 3 : (int)(sizeof(abea_event_t) / 4);
 }
 
 int slot_make_parts(abea_chain_slot* s) {
@@ -351,7 +363,8 @@ int stage_align(chain_state& S, abea_chain_slot& sl) {
     const int32_t* h_ne = (const int32_t*)sl.cnt.u8();
     const abea_scalings_t* h_sc = (const abea_scalings_t*)(sl.cnt.u8() + sl.o_sc_cnt);
     size_t n_ev = 0, n_rec = 0;
-    sl.packed = S.opt.packed; sl.tab_on_dstream = S.opt.copy_engine;
+    sl.rec_words = chain_rec_words(S.opt, J->ev_fields); sl.packed = sl.rec_words * 4 != (int)sizeof(abea_event_t);
+    sl.tab_on_dstream = S.opt.copy_engine;
     for (int32_t j = 0; j < m; ++j) {
         int32_t ne = std::max(h_ne[j], 0);
         if (ne > sl.cap[(size_t)j]) {                        /* overflowed its slots: redone after the pipeline, from the int16 staging */
@@ -363,12 +376,12 @@ int stage_align(chain_state& S, abea_chain_slot& sl) {
             ne = 0;
         }
         sl.ne[(size_t)j] = ne;
-        /* a packed table starts on a multiple of 4 records (the pack kernel stores 4 records = 48 bytes per thread) */
+        /* a packed table starts on a multiple of 4 records (the pack kernels store 4 records = 48 / 32 / 16 bytes per thread) */
         sl.out_ptr[(size_t)j] = (int64_t)n_rec; n_ev += (size_t)ne; n_rec += sl.packed ? ((size_t)ne + 3) / 4 * 4 : (size_t)ne;
         if (want_sc) sl.est[(size_t)j] = h_sc[j];
     }
     sl.n_ev = n_ev; sl.n_rec = n_rec;
-    const size_t rec_bytes = sl.packed ? 12 : sizeof(abea_event_t);
+    const size_t rec_bytes = (size_t)sl.rec_words * 4;
     /* ---- compaction and the tables down: [src_ptr][dst_ptr][count] up, one kernel, one copy-out into pinned memory ---- */
     int rc = sl.tab.need(align_up(n_rec * rec_bytes, 16) + 256);
     if (rc) return rc;
@@ -382,7 +395,8 @@ int stage_align(chain_state& S, abea_chain_slot& sl) {
         for (int32_t j = 0; j < m; ++j) { h_idx[j] = sl.ev_ptr[(size_t)j]; h_idx[m + j] = sl.out_ptr[(size_t)j]; h_cnt[j] = sl.ne[(size_t)j]; }
         HIP_TRY(hipMemcpyAsync(sl.d_idx, h_idx, (size_t)m * 20, hipMemcpyHostToDevice, sl.stream));
         if (sl.packed)
-            hipLaunchKernelGGL(abea_ev_pack_kernel, dim3((unsigned)m), dim3(256), 0, sl.stream, (int)m, (const abea_event_t*)sl.d_ev,
+            hipLaunchKernelGGL(sl.rec_words == 3 ? abea_ev_pack_kernel : sl.rec_words == 2 ? abea_ev_pack8_kernel : abea_ev_pack4_kernel,
+                               dim3((unsigned)m), dim3(256), 0, sl.stream, (int)m, (const abea_event_t*)sl.d_ev,
                                (const int64_t*)sl.d_idx, (const int64_t*)(sl.d_idx + m), (const int32_t*)(sl.d_idx + 2 * (size_t)m), (uint4*)sl.d_evc);
         else
             hipLaunchKernelGGL(abea_ev_compact_kernel, dim3((unsigned)m), dim3(256), 0, sl.stream, (int)m, (const abea_event_t*)sl.d_ev,
@@ -507,20 +521,33 @@ void not_aligned(const abea_chain_job* J, int32_t i, const abea_scalings_t& est)
     J->n_event_alignment[i] = 0;
 }
 
-/* event_t from the 12-byte records the tables crossed PCIe in: {uint32 start, float mean, float stdv}.  The events of a read tile
- * [0, n_samples) (events.c:466-513: event j runs from peak j-1 to peak j, the first from 0, the last to n_samples), so the end of an
- * event is the start of its successor IN DETECTION ORDER — the next record, or the previous one in an RNA table, which event_single
- * reversed (f5c.c:711-719) — and length = (float)(end - start), the very expression of events.c:498. */
-void unpack_events(const uint32_t* rec, size_t ne, uint64_t n_samples, bool rna, abea_event_t* out) {
+/* event_t from the packed records the tables crossed PCIe in, `words` 32-bit words per event: {uint32 start, float mean, float stdv}
+ * (ABEA_EV_FIELDS_ALL), {start, mean} (NO_STDV) or {start} (LAYOUT); a field the record does not carry is written as +0.0f.  The
+ * events of a read tile [0, n_samples) (events.c:466-513: event j runs from peak j-1 to peak j, the first from 0, the last to
+ * n_samples), so the end of an event is the start of its successor IN DETECTION ORDER — the next record, or the previous one in an
+ * RNA table, which event_single reversed (f5c.c:711-719) — and length = (float)(end - start), the very expression of events.c:498. */
+void unpack_events(const uint32_t* rec, int words, size_t ne, uint64_t n_samples, bool rna, abea_event_t* out) {
     for (size_t p = 0; p < ne; ++p) {
-        const uint64_t start = rec[3 * p];
-        const uint64_t end = !rna ? (p + 1 < ne ? (uint64_t)rec[3 * (p + 1)] : n_samples) : (p > 0 ? (uint64_t)rec[3 * (p - 1)] : n_samples);
+        const uint64_t start = rec[words * p];
+        const uint64_t end = !rna ? (p + 1 < ne ? (uint64_t)rec[words * (p + 1)] : n_samples) : (p > 0 ? (uint64_t)rec[words * (p - 1)] : n_samples);
         /* three 8-byte words: event_t is 20 bytes of fields + 4 of tail padding, written as zero (a caller that dumps or compares
          * whole structs must not see stack garbage there) */
         const float length = (float)(end - start);
         uint32_t lb; memcpy(&lb, &length, 4);
-        const uint64_t w[3] = {start, (uint64_t)lb | ((uint64_t)rec[3 * p + 1] << 32), (uint64_t)rec[3 * p + 2]};
+        const uint64_t mean = words >= 2 ? rec[words * p + 1] : 0u, stdv = words >= 3 ? rec[words * p + 2] : 0u;
+        const uint64_t w[3] = {start, (uint64_t)lb | (mean << 32), stdv};
         memcpy(out + p, w, sizeof w);
+    }
+}
+
+/* a whole event_t table cut down to a field selection in place (the redo path of overflowed tables brings whole tables down):
+ * the same three words as unpack_events writes, unselected fields and the tail padding zero */
+void mask_events(abea_event_t* t, size_t ne, uint32_t ev_fields) {
+    if (ev_fields == ABEA_EV_FIELDS_ALL) return;
+    for (size_t p = 0; p < ne; ++p) {
+        uint32_t lb, mb; memcpy(&lb, &t[p].length, 4); memcpy(&mb, &t[p].mean, 4);
+        const uint64_t w[3] = {t[p].start, (uint64_t)lb | (ev_fields == ABEA_EV_FIELDS_NO_STDV ? (uint64_t)mb << 32 : 0u), 0u};
+        memcpy(t + p, w, sizeof w);
     }
 }
 
@@ -539,7 +566,7 @@ int slot_finish(chain_state& S, abea_chain_slot& sl) {
     S.log("scatter", sl.chunk_no, sl.m, sl.n_ev);
     const int32_t m = sl.m;
     const abea_event_t* h_ev = (const abea_event_t*)sl.tab.p;
-    const uint32_t* h_rec = (const uint32_t*)sl.tab.p;                        /* packed form: 3 words per event */
+    const uint32_t* h_rec = (const uint32_t*)sl.tab.p;                        /* packed form: rec_words words per event */
     const bool packed = sl.packed, rna = J->rna != 0;
     /* the result block exists in process mode only (event_db alone reads none of it) */
     const uint8_t* const dnb = J->align ? sl.dn.u8() : nullptr;
@@ -563,7 +590,7 @@ int slot_finish(chain_state& S, abea_chain_slot& sl) {
             abea_event_t* t = (abea_event_t*)malloc(std::max<size_t>(ne, 1) * sizeof(abea_event_t));
             if (!t) { S.oom.store(true); continue; }
             if (!packed) memcpy(t, h_ev + sl.out_ptr[(size_t)j], ne * sizeof(abea_event_t));
-            else unpack_events(h_rec + (size_t)sl.out_ptr[(size_t)j] * 3, ne, (uint64_t)sl.ns32[(size_t)j], rna, t);
+            else unpack_events(h_rec + (size_t)sl.out_ptr[(size_t)j] * (size_t)sl.rec_words, sl.rec_words, ne, (uint64_t)sl.ns32[(size_t)j], rna, t);
             J->events[i] = t; J->n_events[i] = ne;
             if (J->scalings_estimated && want_sc) J->scalings_estimated[i] = sl.est[(size_t)j];
             if (!J->align) { if (J->scalings) J->scalings[i] = sl.est[(size_t)j]; continue; }
@@ -690,7 +717,10 @@ int redo_overflowed(chain_state& S) {
         if (rc) return rc;
         S.st.event_ms += c->stats.event_ms;
     }
-    if (!J->align || S.redo.empty()) return ABEA_OK;
+    /* the redone tables came down whole: cut them to the selection once nothing reads them any more — the alignment below reads
+     * their means (a read's table must not depend on whether it was redone) */
+    auto mask_redone = [&]() { for (const redo_read& r : S.redo) mask_events(J->events[r.idx], (size_t)J->n_events[r.idx], J->ev_fields); };
+    if (!J->align || S.redo.empty()) { mask_redone(); return ABEA_OK; }
     /* align_db + scaling_db for them through the host entry (their tables are host tables now) */
     const int32_t n = (int32_t)S.redo.size();
     std::vector<const char*> rd((size_t)n); std::vector<int32_t> rl((size_t)n), npairs((size_t)n), flag((size_t)n), nal((size_t)n);
@@ -727,6 +757,7 @@ int redo_overflowed(chain_state& S) {
         J->n_event_alignment[i] = nal[(size_t)q];
         if (npairs[(size_t)q] <= 0 && mp[(size_t)q]) { free(mp[(size_t)q]); J->base_to_event_map[i] = nullptr; }
     }
+    mask_redone();
     return ABEA_OK;
 }
 
@@ -830,7 +861,7 @@ int abea_chain_run(abea_ctx* c, const abea_chain_job* J, const int32_t* mine, in
             }
             const size_t m = ck.second - ck.first;
             up_max = std::max(up_max, align_up(align_up(n_sig * 2, 256) + n_seq, 256));
-            tab_max = std::max(tab_max, align_up((n_slot + 3 * m) * (S.opt.packed ? 12 : sizeof(abea_event_t)), 16) + 256);
+            tab_max = std::max(tab_max, align_up((n_slot + 3 * m) * (size_t)chain_rec_words(S.opt, J->ev_fields) * 4, 16) + 256);
             cnt_max = std::max(cnt_max, align_up(align_up(m * 4, 256) + m * sizeof(abea_scalings_t), 256));
             desc_max = std::max(desc_max, m * 24 + 256 + (J->align ? align_up(m * sizeof(abea_read_desc), 256) + align_up(m * sizeof(abea_scalings_t), 256) + align_up(m * 4, 256) : 0));
             if (J->align) dn_max = std::max(dn_max, m * (4 + sizeof(abea_read_diag) + sizeof(abea_scalings_t) + 8 + 4 + 4 + 8) + n_code * 4 + n_kmer + 10 * 256);

@@ -78,7 +78,7 @@ void abea_chain_release(abea_ctx* c);      /* abea_chain.cpp */
 /* what the raw-signal pipeline works on: the fields of abea_events_host_batch / abea_process_batch (include/abea.h), one view
  * for both entries.  align == false: event_db only (scalings = the method-of-moments estimate, may be NULL; read may be NULL
  * with it).  align == true: event_db -> align_db -> scaling_db; every output array below must be present except pairs / diag /
- * scalings_estimated. */
+ * scalings_estimated.  Every device of a multi-device context gets the same job, the field selection with it. */
 struct abea_chain_job {
     int32_t n_reads;
     float* const* rawptr; const int64_t* n_samples; const float* offset; const float* range; const float* digitisation;
@@ -89,6 +89,7 @@ struct abea_chain_job {
     bool align;
     abea_pair_t** pairs; int32_t* n_pairs; abea_read_diag* diag; abea_index_pair_t** base_to_event_map;
     double* events_per_base; int32_t* read_stat_flag; int32_t* n_event_alignment; int32_t min_num_events_to_rescale;
+    uint32_t ev_fields;            /* ABEA_EV_FIELDS_*: which fields of the tables come back (validated by the entries) */
 };
 /* the pipeline on ONE device context over reads mine[0..n_mine) (NULL = all), the caller holds the context (abea_chain.cpp) */
 int abea_chain_run(abea_ctx* c, const abea_chain_job* J, const int32_t* mine, int32_t n_mine, abea_stats* st_out);

@@ -3,6 +3,7 @@
  *   abea_events_batch_host   event_db  = pthread_db(event_single)   src/f5c.c:682-734
  *   abea_process_batch_host  process_db_rsq = event_db -> align_db -> scaling_db   src/resquiggle.c:283-315
  *                            (process_db runs the same three steps first, src/f5c.c:907-936)
+ *   ..._fields               the same two, handing back only the event-table fields the caller reads (ABEA_EV_FIELDS_*)
  *   abea_rsq_format_batch    output_db_rsq's loop over the batch   src/resquiggle.c:319-449
  *
  * f5c holds a read's raw signal as FLOAT ADC counts (signal_t.rawptr, src/f5c.h:276-286: the slow5 / fast5 readers widen
@@ -69,11 +70,28 @@ int chain_over_devices(abea_ctx* c, const abea_chain_job* J, abea_stats* st_out)
     return ABEA_OK;
 }
 
+/* ABEA_EV_FIELDS_* (include/abea.h); checked before anything else is touched */
+bool ev_fields_valid(uint32_t ev_fields) {
+    return ev_fields == ABEA_EV_FIELDS_ALL || ev_fields == ABEA_EV_FIELDS_NO_STDV || ev_fields == ABEA_EV_FIELDS_LAYOUT;
+}
+int ev_fields_fail(const char* who, uint32_t ev_fields) {
+    return abea_fail(ABEA_EINVAL, "%s: ev_fields %u is none of ABEA_EV_FIELDS_ALL (0), ABEA_EV_FIELDS_NO_STDV (1), ABEA_EV_FIELDS_LAYOUT (2)",
+                     who, ev_fields);
+}
+
 }  // namespace
 
 extern "C" int abea_events_batch_host(abea_ctx* c, const abea_events_host_batch* B) {
+    return abea_events_batch_host_fields(c, B, ABEA_EV_FIELDS_ALL);
+}
+
+extern "C" int abea_events_batch_host_fields(abea_ctx* c, const abea_events_host_batch* B, uint32_t ev_fields) {
     if (!c || !B) return abea_fail(ABEA_EINVAL, "null argument");
     if (B->n_reads < 0) return abea_fail(ABEA_EINVAL, "n_reads < 0");
+    if (!ev_fields_valid(ev_fields)) {                   /* the failure contract: no table handed back */
+        for (int32_t i = 0; i < B->n_reads; ++i) { if (B->events) B->events[i] = nullptr; if (B->n_events) B->n_events[i] = 0; }
+        return ev_fields_fail("abea_events_batch_host_fields", ev_fields);
+    }
     if (B->n_reads == 0) return ABEA_OK;
     if (!B->rawptr || !B->n_samples || !B->offset || !B->range || !B->digitisation || !B->events || !B->n_events)
         return abea_fail(ABEA_EINVAL, "abea_events_batch_host: null array");
@@ -86,7 +104,7 @@ extern "C" int abea_events_batch_host(abea_ctx* c, const abea_events_host_batch*
     J.n_reads = B->n_reads; J.rawptr = B->rawptr; J.n_samples = B->n_samples; J.offset = B->offset; J.range = B->range;
     J.digitisation = B->digitisation; J.read = B->scalings ? B->read : nullptr; J.read_len = B->read_len; J.rna = B->rna;
     J.signal_to_pa_in_place = B->signal_to_pa_in_place; J.events = B->events; J.n_events = B->n_events; J.scalings = B->scalings;
-    J.align = false;
+    J.align = false; J.ev_fields = ev_fields;
     abea_stats st;
     const int rc = chain_over_devices(c, &J, &st);
     if (rc) {                                            /* nothing half-built is handed back */
@@ -98,9 +116,22 @@ extern "C" int abea_events_batch_host(abea_ctx* c, const abea_events_host_batch*
 }
 
 extern "C" int abea_process_batch_host(abea_ctx* c, const abea_process_batch* P) {
+    return abea_process_batch_host_fields(c, P, ABEA_EV_FIELDS_ALL);
+}
+
+extern "C" int abea_process_batch_host_fields(abea_ctx* c, const abea_process_batch* P, uint32_t ev_fields) {
     if (!c || !P) return abea_fail(ABEA_EINVAL, "null argument");
     const int32_t n = P->n_reads;
     if (n < 0) return abea_fail(ABEA_EINVAL, "n_reads < 0");
+    if (!ev_fields_valid(ev_fields)) {                   /* the failure contract: no table, pair list or map handed back */
+        for (int32_t i = 0; i < n; ++i) {
+            if (P->events) P->events[i] = nullptr;
+            if (P->n_events) P->n_events[i] = 0;
+            if (P->pairs) P->pairs[i] = nullptr;
+            if (P->base_to_event_map) P->base_to_event_map[i] = nullptr;
+        }
+        return ev_fields_fail("abea_process_batch_host_fields", ev_fields);
+    }
     if (n == 0) return ABEA_OK;
     if (!P->rawptr || !P->n_samples || !P->offset || !P->range || !P->digitisation || !P->read || !P->read_len || !P->events ||
         !P->n_events || !P->scalings || !P->n_pairs || !P->base_to_event_map || !P->events_per_base || !P->read_stat_flag ||
@@ -120,7 +151,7 @@ extern "C" int abea_process_batch_host(abea_ctx* c, const abea_process_batch* P)
     J.scalings = P->scalings; J.scalings_estimated = P->scalings_estimated; J.align = true;
     J.pairs = P->pairs; J.n_pairs = P->n_pairs; J.diag = P->diag; J.base_to_event_map = P->base_to_event_map;
     J.events_per_base = P->events_per_base; J.read_stat_flag = P->read_stat_flag; J.n_event_alignment = P->n_event_alignment;
-    J.min_num_events_to_rescale = P->min_num_events_to_rescale;
+    J.min_num_events_to_rescale = P->min_num_events_to_rescale; J.ev_fields = ev_fields;
     abea_stats st;
     const int rc = chain_over_devices(c, &J, &st);
     if (rc) {

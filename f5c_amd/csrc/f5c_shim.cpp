@@ -142,7 +142,9 @@ static void shim_need_signal(const abea_f5c_db* db, const char* who) {
     }
 }
 
-extern "C" void abea_f5c_event_db(abea_f5c_core* core, abea_f5c_db* db) {
+extern "C" void abea_f5c_event_db(abea_f5c_core* core, abea_f5c_db* db) { abea_f5c_event_db_fields(core, db, ABEA_EV_FIELDS_ALL); }
+
+extern "C" void abea_f5c_event_db_fields(abea_f5c_core* core, abea_f5c_db* db, uint32_t ev_fields) {
     shim_need_signal(db, __func__);
     const int32_t n = db->n_bam_rec;
     std::vector<abea_event_t*> ev((size_t)n);
@@ -153,7 +155,7 @@ extern "C" void abea_f5c_event_db(abea_f5c_core* core, abea_f5c_db* db) {
     eb.digitisation = db->digitisation; eb.read = db->read; eb.read_len = db->read_len; eb.rna = core->rna;
     eb.signal_to_pa_in_place = 1;
     eb.events = ev.data(); eb.n_events = n_ev.data(); eb.scalings = db->scalings;
-    if (abea_events_batch_host((abea_ctx*)core->cuda, &eb) != ABEA_OK) SHIM_DIE("abea_events_batch_host");
+    if (abea_events_batch_host_fields((abea_ctx*)core->cuda, &eb, ev_fields) != ABEA_OK) SHIM_DIE("abea_events_batch_host_fields");
     for (int32_t i = 0; i < n; ++i) {
         db->et[i].event = ev[(size_t)i]; db->et[i].n = (size_t)n_ev[(size_t)i];
         db->et[i].start = 0; db->et[i].end = (size_t)n_ev[(size_t)i];           /* events.c:576-580 */
@@ -167,7 +169,9 @@ extern "C" void abea_f5c_event_db(abea_f5c_core* core, abea_f5c_db* db) {
     core->event_time += st.total_ms * 1e-3;
 }
 
-extern "C" void abea_f5c_process(abea_f5c_core* core, abea_f5c_db* db) {
+extern "C" void abea_f5c_process(abea_f5c_core* core, abea_f5c_db* db) { abea_f5c_process_fields(core, db, ABEA_EV_FIELDS_ALL); }
+
+extern "C" void abea_f5c_process_fields(abea_f5c_core* core, abea_f5c_db* db, uint32_t ev_fields) {
     shim_need_signal(db, __func__);
     if (!db->base_to_event_map || !db->events_per_base || !db->read_stat_flag || !db->n_event_alignment) {
         fprintf(stderr, "[%s::ERROR] the db view lacks the scaling_single outputs\n", __func__);
@@ -186,7 +190,7 @@ extern "C" void abea_f5c_process(abea_f5c_core* core, abea_f5c_db* db) {
     pb.base_to_event_map = db->base_to_event_map; pb.events_per_base = db->events_per_base;
     pb.read_stat_flag = db->read_stat_flag; pb.n_event_alignment = db->n_event_alignment;
     pb.min_num_events_to_rescale = core->min_num_events_to_rescale;
-    if (abea_process_batch_host((abea_ctx*)core->cuda, &pb) != ABEA_OK) SHIM_DIE("abea_process_batch_host");
+    if (abea_process_batch_host_fields((abea_ctx*)core->cuda, &pb, ev_fields) != ABEA_OK) SHIM_DIE("abea_process_batch_host_fields");
     for (int32_t i = 0; i < n; ++i) {
         db->et[i].event = ev[(size_t)i]; db->et[i].n = (size_t)n_ev[(size_t)i];
         db->et[i].start = 0; db->et[i].end = (size_t)n_ev[(size_t)i];

@@ -268,6 +268,22 @@ typedef struct {
 } abea_process_batch;
 int abea_process_batch_host(abea_ctx* ctx, const abea_process_batch* batch);
 
+/* ---- which event-table fields the two entries above hand back ----
+ * The event tables are the largest transfer of the raw-signal entries (24-byte event_t per event on the host, 12 bytes of it
+ * over PCIe), and most of f5c's consumers read only part of each event: resquiggle's output_db_rsq reads start and length
+ * (src/resquiggle.c:373-380), call-methylation's profile HMM reads the means (src/hmm.c:85), eventalign everything.  The _fields
+ * entries take the selection; only the selected fields cross PCIe (ALL 12, NO_STDV 8, LAYOUT 4 bytes per event).  The tables
+ * are still one malloc()ed abea_event_t array per read, with every field that was not selected written as +0.0f (all bits zero)
+ * and the tail padding zero.  n_events, the method-of-moments scalings and — process entry — every other output (pairs, maps,
+ * recalibrated scalings, flags, events_per_base, n_event_alignment) do not depend on the selection: the alignment reads the
+ * means from the tables the detector left in HBM.  Any other value returns ABEA_EINVAL before any work, with every events[i]
+ * NULL.  abea_events_batch_host / abea_process_batch_host are these calls with ABEA_EV_FIELDS_ALL. */
+#define ABEA_EV_FIELDS_ALL     0u   /* start, length, mean, stdv: what abea_events_batch_host / abea_process_batch_host return */
+#define ABEA_EV_FIELDS_NO_STDV 1u   /* start, length, mean; stdv = +0.0f   (call-methylation) */
+#define ABEA_EV_FIELDS_LAYOUT  2u   /* start, length; mean = stdv = +0.0f  (resquiggle) */
+int abea_events_batch_host_fields(abea_ctx* ctx, const abea_events_host_batch* batch, uint32_t ev_fields);
+int abea_process_batch_host_fields(abea_ctx* ctx, const abea_process_batch* batch, uint32_t ev_fields);
+
 /* ---- resquiggle output of one read (row N3): the per-read body of output_db_rsq() (src/resquiggle.c:319-449) ----
  * fmt 0 = TSV (one line per k-mer: read_id, k-mer index, first sample, one-past-last sample or "."), fmt 1 = PAF
  * (one line; the ss:Z: string encodes matched samples "n,", skipped samples "nI", k-mers without events "nD").

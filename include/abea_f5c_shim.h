@@ -85,6 +85,11 @@ void abea_f5c_align_wait(abea_f5c_core* core, void* handle);
 void abea_f5c_event_db(abea_f5c_core* core, abea_f5c_db* db);
 /* process_db_rsq (resquiggle.c:283-315) = event_db -> align_db -> scaling_db in one call; every output of the three. */
 void abea_f5c_process(abea_f5c_core* core, abea_f5c_db* db);
+/* the same two calls handing back only the event-table fields ev_fields selects (ABEA_EV_FIELDS_*, include/abea.h): the others
+ * are +0.0f in db->et[i].event.  resquiggle wants ABEA_EV_FIELDS_LAYOUT, call-methylation ABEA_EV_FIELDS_NO_STDV, eventalign
+ * ABEA_EV_FIELDS_ALL (= abea_f5c_event_db / abea_f5c_process).  A value that is none of the three exits like every error here. */
+void abea_f5c_event_db_fields(abea_f5c_core* core, abea_f5c_db* db, uint32_t ev_fields);
+void abea_f5c_process_fields(abea_f5c_core* core, abea_f5c_db* db, uint32_t ev_fields);
 void abea_f5c_free(abea_f5c_core* core);
 
 #ifdef __cplusplus
