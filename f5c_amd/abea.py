@@ -19,10 +19,10 @@ EXPORTS = ["abea_init", "abea_init_multi", "abea_device_count", "abea_free", "ab
            "abea_host_plan_chunks", "abea_host_plan_threads", "abea_set_inflight", "abea_align_batch_host_submit",
            "abea_align_batch_host_wait", "abea_events_batch_host", "abea_process_batch_host", "abea_rsq_format_batch",
            "abea_hmm_score_batch_device", "abea_expand_kmer_counts_to_map", "abea_flatten_event_means", "abea_link_probe",
-           "abea_events_batch_host_fields", "abea_process_batch_host_fields"]
+           "abea_events_batch_host_fields", "abea_process_batch_host_fields", "abea_meth_batch_host", "abea_meth_format_batch"]
 SHIM_EXPORTS = ["abea_f5c_init", "abea_f5c_align", "abea_f5c_align_scale", "abea_f5c_free", "abea_f5c_align_submit",
                 "abea_f5c_align_wait", "abea_f5c_event_db", "abea_f5c_process", "abea_f5c_event_db_fields",
-                "abea_f5c_process_fields"]      # include/abea_f5c_shim.h
+                "abea_f5c_process_fields", "abea_f5c_meth"]      # include/abea_f5c_shim.h
 
 # which event-table fields the raw-signal entries hand back (ABEA_EV_FIELDS_*, include/abea.h); unselected fields come back as +0.0f
 EV_FIELDS_ALL = 0        # start, length, mean, stdv (eventalign)
@@ -116,6 +116,53 @@ class HmmJob(C.Structure):
                 ("rc", C.c_uint8), ("pad", C.c_uint16), ("hmm_flags", C.c_uint32), ("events_per_base", C.c_double)]
 
 
+# abea_meth_site_t (include/abea.h): one scored CpG group of a read (ScoredSite, meth.c:575-598)
+SITE_DT = np.dtype([("start_position", "<i4"), ("end_position", "<i4"), ("n_cpg", "<i4"), ("strands_scored", "<i4"),
+                    ("ll_methylated", "<f4"), ("ll_unmethylated", "<f4")])
+
+
+class _MethBatch(C.Structure):
+    """abea_meth_batch (include/abea.h)"""
+    _fields_ = [("n_reads", C.c_int32), ("fasta_cache", C.c_void_p), ("pos", C.c_void_p), ("cigar", C.c_void_p),
+                ("n_cigar", C.c_void_p), ("is_rev", C.c_void_p), ("read_len", C.c_void_p), ("events", C.c_void_p),
+                ("n_events", C.c_void_p), ("base_to_event_map", C.c_void_p), ("scalings", C.c_void_p),
+                ("events_per_base", C.c_void_p), ("read_stat_flag", C.c_void_p), ("n_sites", C.c_void_p), ("sites", C.c_void_p)]
+
+
+def _ptrs(arrs):
+    """uint64 array of the data addresses of a list of numpy arrays (0 for None / empty)"""
+    return np.array([a.ctypes.data if a is not None and a.size else 0 for a in arrs], dtype=np.uint64)
+
+
+def meth_format(contigs, read_names, is_rev, segments, pos, sites, kmer_size, version=1, header=False, clip_start=-1, clip_end=-1,
+                read_stat_flag=None):
+    """The text output_db prints for call-methylation mode 0 (abea_meth_format_batch; f5c.c:1033-1062), host-only.
+    sites: per read a SITE_DT array (what AbeaContext.meth_batch returns) or None."""
+    lib = load_library()
+    fn = lib.abea_meth_format_batch
+    fn.restype = C.c_int64
+    fn.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int32] + [C.c_void_p] * 8 + [C.c_uint32, C.c_int32, C.c_int32, C.c_void_p]
+    n = len(read_names)
+    enc = lambda xs: [x.encode() if isinstance(x, str) else bytes(x) for x in xs]
+    keep = [C.create_string_buffer(b) for b in enc(contigs) + enc(read_names) + enc(segments)]
+    cp = np.array([C.addressof(b) for b in keep], dtype=np.uint64)
+    st = [np.ascontiguousarray(s, dtype=SITE_DT) if s is not None else np.zeros(0, dtype=SITE_DT) for s in sites]
+    n_sites = np.array([len(s) for s in st], dtype=np.int32)
+    sp = _ptrs(st)
+    rev = np.ascontiguousarray(is_rev, dtype=np.uint8)
+    p = np.ascontiguousarray(pos, dtype=np.int32)
+    flag = None if read_stat_flag is None else np.ascontiguousarray(read_stat_flag, dtype=np.int32)
+    args = [n, _p(cp[:n]), _p(cp[n:2 * n]), _p(rev), _p(cp[2 * n:]), _p(p), None if flag is None else _p(flag), _p(n_sites), _p(sp),
+            kmer_size, clip_start, clip_end]
+    need = fn(None, 0, version, 1 if header else 0, *args, None)
+    if need < 0:
+        raise AbeaError(f"abea_meth_format_batch: bad argument ({need})")
+    buf = C.create_string_buffer(int(need) + 1)
+    got = fn(buf, len(buf), version, 1 if header else 0, *args, None)
+    assert got == need
+    return buf.value.decode()
+
+
 class Stats(C.Structure):
     _fields_ = [("pre_ms", C.c_double), ("fill_ms", C.c_double), ("trace_ms", C.c_double),
                 ("h2d_ms", C.c_double), ("d2h_ms", C.c_double), ("host_ms", C.c_double), ("event_ms", C.c_double),
@@ -129,7 +176,8 @@ class Stats(C.Structure):
                 ("flatten_ms", C.c_double), ("unflatten_ms", C.c_double), ("wait_ms", C.c_double),
                 ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64), ("n_devices", C.c_int32),
                 ("host_threads", C.c_int32), ("plan_ms", C.c_double), ("setup_ms", C.c_double),
-                ("gpu_busy_ms", C.c_double)]
+                ("gpu_busy_ms", C.c_double),
+                ("meth_ms", C.c_double), ("meth_groups", C.c_int64), ("meth_groups_skipped", C.c_int64)]
 
     def asdict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -511,6 +559,59 @@ class AbeaContext:
         self._chk(fn(self._h, C.cast(arr, C.c_void_p), n, _p(m), kmer_size, _p(out)),
                   "abea_hmm_score_batch_device" if device_events else "abea_hmm_score_batch_host")
         return out[:n]
+
+    # ---- call-methylation, mode 0 (meth_single, src/f5c.c:885-890) ----
+    def meth_batch(self, segments, pos, cigars, is_rev, read_len, events, base_to_event_map, scalings, events_per_base, cpgmodel,
+                   kmer_size, read_stat_flag=None, n_events=None):
+        """abea_meth_batch_host: per read a SITE_DT array of its scored CpG groups (empty for flagged reads or reads with none).
+        segments: the reference segments from each read's pos (bytes / str); cigars: uint32 CIGAR words per read; events: per read
+        an EVENT_DT array, or a uint64 array of event_t* (with n_events); base_to_event_map: per read an int32 [K,2] array, or a
+        uint64 array of index_pair_t*; scalings: SCAL_DT [n]; cpgmodel: MODEL_DT [5^k]."""
+        n = len(segments)
+        keep = [C.create_string_buffer(x.encode() if isinstance(x, str) else bytes(x)) for x in segments]
+        seg_pp = np.array([C.addressof(b) for b in keep], dtype=np.uint64)
+        cig = [np.ascontiguousarray(c, dtype=np.uint32) for c in cigars]
+        cig_pp, n_cig = _ptrs(cig), np.array([len(c) for c in cig], dtype=np.uint32)
+        if isinstance(events, np.ndarray) and events.dtype == np.uint64:
+            ev_pp, ne = events, np.ascontiguousarray(n_events, dtype=np.uint64)
+        else:
+            evs = [np.ascontiguousarray(e, dtype=EVENT_DT) for e in events]
+            ev_pp, ne = _ptrs(evs), np.array([len(e) for e in evs], dtype=np.uint64)
+            keep.append(evs)
+        if isinstance(base_to_event_map, np.ndarray) and base_to_event_map.dtype == np.uint64:
+            map_pp = base_to_event_map
+        else:
+            maps = [None if m is None else np.ascontiguousarray(np.asarray(m).view(np.int32).reshape(-1, 2)) for m in base_to_event_map]
+            map_pp = _ptrs(maps)
+            keep.append(maps)
+        posa = np.ascontiguousarray(pos, dtype=np.int32)
+        rev = np.ascontiguousarray(is_rev, dtype=np.uint8)
+        rl = np.ascontiguousarray(read_len, dtype=np.int32)
+        sc = np.ascontiguousarray(scalings, dtype=SCAL_DT)
+        epb = np.ascontiguousarray(events_per_base, dtype=np.float64)
+        flag = None if read_stat_flag is None else np.ascontiguousarray(read_stat_flag, dtype=np.int32)
+        m = np.ascontiguousarray(cpgmodel, dtype=MODEL_DT)
+        assert len(m) == 5 ** kmer_size
+        n_sites = np.zeros(max(n, 1), dtype=np.int32)
+        sites_pp = np.zeros(max(n, 1), dtype=np.uint64)
+        mb = _MethBatch(n, _p(seg_pp), _p(posa), _p(cig_pp), _p(n_cig), _p(rev), _p(rl), _p(ev_pp), _p(ne), _p(map_pp), _p(sc),
+                        _p(epb), None if flag is None else _p(flag), _p(n_sites), _p(sites_pp))
+        fn = self._lib.abea_meth_batch_host
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(_MethBatch), C.c_void_p, C.c_uint32]
+        self._chk(fn(self._h, C.byref(mb), _p(m), kmer_size), "abea_meth_batch_host")
+        libc = C.CDLL(None)
+        libc.free.argtypes = [C.c_void_p]
+        libc.free.restype = None
+        out = []
+        for i in range(n):
+            ns, ptr = int(n_sites[i]), int(sites_pp[i])
+            if ns == 0 or not ptr:
+                out.append(np.zeros(0, dtype=SITE_DT))
+                continue
+            out.append(np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(ns * SITE_DT.itemsize,)).view(SITE_DT).copy())
+            libc.free(ptr)
+        return out
 
     # ---- device-resident flattened batch ----
     @staticmethod

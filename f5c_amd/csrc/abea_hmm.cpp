@@ -11,21 +11,63 @@
 extern "C" __global__ void abea_hmm_forward_kernel(int, int, int, const abea_hmm_job*, const char*, const float*,
                                                    const abea_model_t*, int, const float*, const float*, float*, float*);
 
-struct abea_hmm_state {                    /* per context, created on first use */
-    float* d_tbl = nullptr;                /* p7_FLogsum table (logsum.h:33-48), built with glibc on the host */
-    abea_model_t* d_model = nullptr; size_t model_entries = 0;
-    uint8_t* pin = nullptr; size_t pin_cap = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-};
-
 void abea_hmm_release(abea_ctx* c) {
     abea_hmm_state* s = c->hmm;
     if (!s) return;
-    hipFree(s->d_tbl); hipFree(s->d_model); hipHostFree(s->pin);
-    if (s->e0) hipEventDestroy(s->e0);
-    if (s->e1) hipEventDestroy(s->e1);
+    hipFree(s->d_tbl); hipFree(s->d_model); hipHostFree(s->pin); hipHostFree(s->mpin);
+    for (hipEvent_t e : {s->e0, s->e1, s->m0, s->m1, s->m2}) if (e) hipEventDestroy(e);
     delete s;
     c->hmm = nullptr;
+}
+
+/* the context's HMM state (log-sum table, timing events) created on first use, and the CpG model copied to the device; used by
+ * abea_meth.cpp too */
+int abea_hmm_prepare(abea_ctx* c, const abea_model_t* cpgmodel, uint32_t kmer_size) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->hmm) {
+        /* built aside and published only when complete: a failure half-way must not leave a state the next call
+         * would take for initialised (round-2 advisor finding) */
+        c->hmm = new abea_hmm_state();
+        struct undo { abea_ctx* c; bool ok = false; ~undo() { if (!ok) abea_hmm_release(c); } } guard{c};
+        std::vector<float> tbl(ABEA_HMM_TBL);
+        for (int i = 0; i < ABEA_HMM_TBL; i++) tbl[(size_t)i] = (float)log(1. + exp((double)-i / 1000.f));   /* logsum.h:44 */
+        HIP_TRY(hipMalloc(&c->hmm->d_tbl, ABEA_HMM_TBL * sizeof(float)));
+        HIP_TRY(hipMemcpy(c->hmm->d_tbl, tbl.data(), ABEA_HMM_TBL * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipEventCreate(&c->hmm->e0)); HIP_TRY(hipEventCreate(&c->hmm->e1));
+        guard.ok = true;
+    }
+    abea_hmm_state* S = c->hmm;
+    size_t n_model = 1;
+    for (uint32_t i = 0; i < kmer_size; ++i) n_model *= 5;            /* MAX_NUM_KMER_METH: alphabet A,C,G,M,T */
+    if (S->model_entries != n_model) {
+        hipFree(S->d_model); S->d_model = nullptr; S->model_entries = 0;
+        HIP_TRY(hipMalloc(&S->d_model, n_model * sizeof(abea_model_t)));
+        S->model_entries = n_model;
+    }
+    HIP_TRY(hipMemcpyAsync(S->d_model, cpgmodel, n_model * sizeof(abea_model_t), hipMemcpyHostToDevice, c->stream));
+    return ABEA_OK;
+}
+
+/* calculate_transitions (hmm.c:240-310) of a read into a job descriptor; hmm.c is compiled as C++ (Makefile:6), so log() of a
+ * float is logf */
+void abea_hmm_transitions(double events_per_base, abea_hmm_job& d) {
+    float p_stay = 1 - (1 / events_per_base);
+    float p_skip = 0.0025, p_bad = 0.001, p_bad_self = p_bad, p_skip_self = 0.3;
+    float p_mk = p_skip, p_mb = p_bad, p_mm_self = p_stay, p_mm_next = 1.0f - p_mm_self - p_mk - p_mb;
+    float p_bb = p_bad_self, p_bk, p_bm_next, p_bm_self;
+    p_bk = p_bm_next = p_bm_self = (1.0f - p_bb) / 3;
+    float p_kk = p_skip_self, p_km = 1.0f - p_kk;
+    d.lp_mk = logf(p_mk); d.lp_mb = logf(p_mb); d.lp_mm_self = logf(p_mm_self); d.lp_mm_next = logf(p_mm_next);
+    d.lp_bb = logf(p_bb); d.lp_bk = logf(p_bk); d.lp_bm_next = logf(p_bm_next); d.lp_bm_self = logf(p_bm_self);
+    d.lp_kk = logf(p_kk); d.lp_km = logf(p_km);
+}
+
+/* pre_flank (hmm.c:188-233) for windows of up to max_ev events; post_flank[i] = pre_flank[n_events-1-i] term by term (hmm.c:141-185) */
+void abea_hmm_flank(std::vector<float>& flank, int32_t max_ev) {
+    flank.assign((size_t)max_ev + 1, 0.f);
+    flank[0] = log(1 - 0.5);
+    if (max_ev >= 1) flank[1] = log(0.5) + -3.0f + log(1 - 0.9);
+    for (size_t i = 2; i < flank.size(); ++i) flank[i] = log(0.9) + -3.0f + flank[i - 1];
 }
 
 extern "C" __global__ void abea_hmm_gather_kernel(int, const abea_hmm_job*, const int64_t*, const int32_t*, float*);
@@ -53,29 +95,9 @@ static int hmm_score_batch(abea_ctx* c, const abea_hmm_job_t* jobs, int32_t n_jo
     if (n_jobs == 0) return ABEA_OK;
     ABEA_API_ENTER(c, "abea_hmm_score_batch_host");
     const double t_start = abea_now_ms();
-    HIP_TRY(hipSetDevice(c->device));
-    if (!c->hmm) {
-        /* built aside and published only when complete: a failure half-way must not leave a state the next call
-         * would take for initialised (round-2 advisor finding) */
-        c->hmm = new abea_hmm_state();
-        struct undo { abea_ctx* c; bool ok = false; ~undo() { if (!ok) abea_hmm_release(c); } } guard{c};
-        std::vector<float> tbl(ABEA_HMM_TBL);
-        for (int i = 0; i < ABEA_HMM_TBL; i++) tbl[(size_t)i] = (float)log(1. + exp((double)-i / 1000.f));   /* logsum.h:44 */
-        HIP_TRY(hipMalloc(&c->hmm->d_tbl, ABEA_HMM_TBL * sizeof(float)));
-        HIP_TRY(hipMemcpy(c->hmm->d_tbl, tbl.data(), ABEA_HMM_TBL * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipEventCreate(&c->hmm->e0)); HIP_TRY(hipEventCreate(&c->hmm->e1));
-        guard.ok = true;
-    }
+    int prc = abea_hmm_prepare(c, cpgmodel, kmer_size);
+    if (prc) return prc;
     abea_hmm_state* S = c->hmm;
-    size_t n_model = 1;
-    for (uint32_t i = 0; i < kmer_size; ++i) n_model *= 5;            /* MAX_NUM_KMER_METH: alphabet A,C,G,M,T */
-    if (S->model_entries != n_model) {
-        hipFree(S->d_model); S->d_model = nullptr; S->model_entries = 0;
-        HIP_TRY(hipMalloc(&S->d_model, n_model * sizeof(abea_model_t)));
-        S->model_entries = n_model;
-    }
-    HIP_TRY(hipMemcpyAsync(S->d_model, cpgmodel, n_model * sizeof(abea_model_t), hipMemcpyHostToDevice, c->stream));
-
     /* ---- jobs with at most 16 k-mers first (four to a wavefront), then the wide ones ---- */
     std::vector<int32_t> order((size_t)n_jobs);
     std::vector<int32_t> seq_len((size_t)n_jobs), n_ev((size_t)n_jobs);
@@ -131,23 +153,11 @@ static int hmm_score_batch(abea_ctx* c, const abea_hmm_job_t* jobs, int32_t n_jo
             abea_hmm_job& d = desc[(size_t)q];
             d.rc = J.rc ? 1 : 0; d.flags = J.hmm_flags;
             d.scale = J.scaling.scale; d.shift = J.scaling.shift; d.var = J.scaling.var; d.log_var = J.scaling.log_var;
-            /* calculate_transitions (hmm.c:240-310); hmm.c is compiled as C++ (Makefile:6), so log() of a float is logf */
-            float p_stay = 1 - (1 / J.events_per_base);
-            float p_skip = 0.0025, p_bad = 0.001, p_bad_self = p_bad, p_skip_self = 0.3;
-            float p_mk = p_skip, p_mb = p_bad, p_mm_self = p_stay, p_mm_next = 1.0f - p_mm_self - p_mk - p_mb;
-            float p_bb = p_bad_self, p_bk, p_bm_next, p_bm_self;
-            p_bk = p_bm_next = p_bm_self = (1.0f - p_bb) / 3;
-            float p_kk = p_skip_self, p_km = 1.0f - p_kk;
-            d.lp_mk = logf(p_mk); d.lp_mb = logf(p_mb); d.lp_mm_self = logf(p_mm_self); d.lp_mm_next = logf(p_mm_next);
-            d.lp_bb = logf(p_bb); d.lp_bk = logf(p_bk); d.lp_bm_next = logf(p_bm_next); d.lp_bm_self = logf(p_bm_self);
-            d.lp_kk = logf(p_kk); d.lp_km = logf(p_km);
+            abea_hmm_transitions(J.events_per_base, d);
         }
     });
-    /* pre_flank (hmm.c:188-233); post_flank[i] = pre_flank[n_events-1-i] term by term (hmm.c:141-185) */
-    std::vector<float> flank((size_t)max_ev + 1);
-    flank[0] = log(1 - 0.5);
-    if (max_ev >= 1) flank[1] = log(0.5) + -3.0f + log(1 - 0.9);
-    for (size_t i = 2; i < flank.size(); ++i) flank[i] = log(0.9) + -3.0f + flank[i - 1];
+    std::vector<float> flank;
+    abea_hmm_flank(flank, max_ev);
 
     /* ---- staging: [desc][flank][seqs][event windows] up, [scores] down ---- */
     size_t o = 0;

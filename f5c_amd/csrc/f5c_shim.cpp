@@ -201,6 +201,24 @@ extern "C" void abea_f5c_process_fields(abea_f5c_core* core, abea_f5c_db* db, ui
     shim_finish(core, db, false, __func__);              /* the maps of failed reads were released by the library */
 }
 
+extern "C" void abea_f5c_meth(abea_f5c_core* core, abea_f5c_meth_db* db) {
+    if (!core || !db || !core->cuda) { fprintf(stderr, "[%s::ERROR] abea_f5c_init has not run\n", __func__); exit(EXIT_FAILURE); }
+    const int32_t n = db->n_bam_rec;
+    std::vector<const abea_event_t*> ev((size_t)std::max(n, 0));
+    std::vector<uint64_t> n_ev((size_t)std::max(n, 0));
+    for (int32_t i = 0; i < n; ++i) { ev[(size_t)i] = db->et[i].event; n_ev[(size_t)i] = db->et[i].n; }
+    abea_meth_batch mb;
+    memset(&mb, 0, sizeof mb);
+    mb.n_reads = n; mb.fasta_cache = db->fasta_cache; mb.pos = db->pos; mb.cigar = db->cigar; mb.n_cigar = db->n_cigar;
+    mb.is_rev = db->is_rev; mb.read_len = db->read_len; mb.events = ev.data(); mb.n_events = n_ev.data();
+    mb.base_to_event_map = db->base_to_event_map; mb.scalings = db->scalings; mb.events_per_base = db->events_per_base;
+    mb.read_stat_flag = db->read_stat_flag; mb.n_sites = db->n_sites; mb.sites = db->sites;
+    if (abea_meth_batch_host((abea_ctx*)core->cuda, &mb, db->cpgmodel, core->kmer_size) != ABEA_OK) SHIM_DIE("abea_meth_batch_host");
+    abea_stats st;
+    abea_get_stats((abea_ctx*)core->cuda, &st);
+    db->meth_time = st.meth_ms * 1e-3;
+}
+
 extern "C" void abea_f5c_free(abea_f5c_core* core) {
     abea_free((abea_ctx*)core->cuda);
     core->cuda = nullptr;

@@ -332,6 +332,49 @@ int abea_hmm_score_batch_host(abea_ctx* ctx, const abea_hmm_job_t* jobs, int32_t
 int abea_hmm_score_batch_device(abea_ctx* ctx, const abea_hmm_job_t* jobs, int32_t n_jobs, const abea_model_t* cpgmodel,
                                 uint32_t kmer_size, float* scores);
 
+/* ---- call-methylation, mode 0 (meth_single -> calculate_methylation_for_read, src/meth.c:473-612, src/f5c.c:885-890) ----
+ * The CpG sites of every read whose read_stat_flag is clear, scored on the GPU: the job builder (CpG groups, the event window of
+ * each through the CIGAR and base_to_event_map, the unmethylated and methylated sequences) runs on the device, the jobs are then
+ * scored as abea_hmm_score_batch_host scores them, bit for bit.  The fields are what f5c holds after scaling_db. */
+typedef struct {
+    int32_t start_position, end_position; /* reference coordinates of the group's first and last CpG (ScoredSite, f5c.h) */
+    int32_t n_cpg, strands_scored;        /* strands_scored is 1 (one strand per read) */
+    float ll_methylated, ll_unmethylated; /* profile_hmm_score of the methylated / unmethylated sequence */
+} abea_meth_site_t;
+typedef struct {
+    int32_t n_reads;
+    const char* const* fasta_cache;       /* db->fasta_cache[i]: the reference segment from record->core.pos, NUL-terminated */
+    const int32_t* pos;                   /* record->core.pos */
+    const uint32_t* const* cigar;         /* bam_get_cigar(record) */
+    const uint32_t* n_cigar;              /* record->core.n_cigar */
+    const uint8_t* is_rev;                /* bam_is_rev(record) */
+    const int32_t* read_len;              /* db->read_len[i] */
+    const abea_event_t* const* events;    /* db->et[i].event: only .mean is read (hmm.c:85) */
+    const uint64_t* n_events;             /* db->et[i].n */
+    abea_index_pair_t* const* base_to_event_map;   /* db->base_to_event_map[i], read_len - k + 1 entries: only .start is read */
+    const abea_scalings_t* scalings;      /* db->scalings[i] */
+    const double* events_per_base;        /* db->events_per_base[i] */
+    const int32_t* read_stat_flag;        /* db->read_stat_flag[i]: reads with a non-zero flag are skipped (f5c.c:886) */
+    int32_t* n_sites;                     /* out: sites of read i */
+    abea_meth_site_t** sites;             /* out: malloc()ed, ordered by start_position; NULL when there are none */
+} abea_meth_batch;
+/* Returns ABEA_EINVAL, with every sites[i] NULL, when a CIGAR holds N (ref skip) or an op get_aligned_segments does not handle,
+ * or a segment holds a byte that is no IUPAC code (the reference exits or asserts).  Reads go to the device in chunks that fit
+ * the arena (ABEA_METH_CHUNK_READS in the environment caps the reads per chunk); a multi-device context splits the reads by
+ * segment length.  Deliberate divergence: a group whose event bound is -1 (no mapped event within 1000 k-mers; the reference
+ * passes (uint32_t)-1 into the HMM) is skipped and counted in abea_stats.meth_groups_skipped. */
+int abea_meth_batch_host(abea_ctx* ctx, const abea_meth_batch* batch, const abea_model_t* cpgmodel, uint32_t kmer_size);
+/* The body of output_db for mode 0 (src/f5c.c:1033-1062) over a batch: every read with a clear read_stat_flag, its sites in order,
+ * for --meth-out-version 1 or 2; the sequence column is cut again from the disambiguated segment, [first CpG - k + 1, last CpG + k).
+ * Sites outside [clip_start, clip_end) are not printed (-1 = no limit).  header != 0 prints the header line of meth_main.c:560-570
+ * first.  snprintf-like (returns the full length, writes at most cap-1 bytes + NUL; out may be NULL with cap 0); n_printed
+ * (optional) = rows printed.  Host-only. */
+int64_t abea_meth_format_batch(char* out, size_t cap, int meth_out_version, int header, int32_t n_reads,
+                               const char* const* contig, const char* const* read_name, const uint8_t* is_rev,
+                               const char* const* fasta_cache, const int32_t* pos, const int32_t* read_stat_flag,
+                               const int32_t* n_sites, const abea_meth_site_t* const* sites, uint32_t kmer_size,
+                               int32_t clip_start, int32_t clip_end, int64_t* n_printed);
+
 /* ---- timing / accounting of the last batch (core_t timing fields, src/f5c.h:457-466) ---- */
 typedef struct {
     double pre_ms, fill_ms, trace_ms;     /* HIP-event kernel times on the library's stream, summed over sub-batches
@@ -359,6 +402,11 @@ typedef struct {
     double gpu_busy_ms;                   /* host batch / raw-signal entries: length of the union of the chunks' kernel intervals on the
                                              GPU's clock (first kernel start .. last kernel end per chunk): total_ms - gpu_busy_ms = time
                                              the device had nothing of this call to run */
+    /* abea_meth_batch_host (appended: the fields above keep their offsets) */
+    double meth_ms;                       /* kernel time of the last call: job builder (both passes) + forward kernel (= hmm_ms) */
+    int64_t meth_groups;                  /* CpG groups scored (two jobs each) */
+    int64_t meth_groups_skipped;          /* groups skipped for a bound of -1 or outside the event table, or a stride against
+                                             the strand, where the reference scores undefined input or asserts */
 } abea_stats;
 int abea_get_stats(abea_ctx* ctx, abea_stats* out);
 /* Multi-device context: the share of the last host batch that ran on device_ids[device]; abea_get_stats() gives the

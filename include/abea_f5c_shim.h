@@ -90,6 +90,29 @@ void abea_f5c_process(abea_f5c_core* core, abea_f5c_db* db);
  * ABEA_EV_FIELDS_ALL (= abea_f5c_event_db / abea_f5c_process).  A value that is none of the three exits like every error here. */
 void abea_f5c_event_db_fields(abea_f5c_core* core, abea_f5c_db* db, uint32_t ev_fields);
 void abea_f5c_process_fields(abea_f5c_core* core, abea_f5c_db* db, uint32_t ev_fields);
+
+/* call-methylation, mode 0: meth_single over a batch (src/f5c.c:885-890 under pthread_db) after abea_f5c_process /
+ * abea_f5c_align_scale.  A struct of its own, so that abea_f5c_db keeps its layout: the slice of db_t that
+ * calculate_methylation_for_read reads, with the bam1_t fields gathered, and the sites it leaves for output_db. */
+typedef struct {
+    int32_t n_bam_rec;
+    char** fasta_cache;                    /* db->fasta_cache */
+    const int32_t* pos;                    /* db->bam_rec[i]->core.pos */
+    const uint32_t* const* cigar;          /* bam_get_cigar(db->bam_rec[i]) */
+    const uint32_t* n_cigar;               /* db->bam_rec[i]->core.n_cigar */
+    const uint8_t* is_rev;                 /* bam_is_rev(db->bam_rec[i]) */
+    int32_t* read_len;                     /* db->read_len */
+    abea_f5c_event_table* et;              /* db->et */
+    abea_index_pair_t** base_to_event_map; /* db->base_to_event_map */
+    abea_scalings_t* scalings;             /* db->scalings */
+    double* events_per_base;               /* db->events_per_base */
+    int32_t* read_stat_flag;               /* db->read_stat_flag: flagged reads are skipped */
+    const abea_model_t* cpgmodel;          /* core->cpgmodel, 5^kmer_size entries (alphabet A,C,G,M,T) */
+    int32_t* n_sites;                      /* out: the sites of read i (db->site_score_map[i]->size()) */
+    abea_meth_site_t** sites;              /* out: malloc()ed per read, ordered by start_position, NULL when none; the caller free()s */
+    double meth_time;                      /* out: seconds of kernel time of the call (job builder + HMM) */
+} abea_f5c_meth_db;
+void abea_f5c_meth(abea_f5c_core* core, abea_f5c_meth_db* db);
 void abea_f5c_free(abea_f5c_core* core);
 
 #ifdef __cplusplus

@@ -12,7 +12,25 @@ from oracle import orc
 
 
 
-def run(budget=60.0, seed=1, ctx=None, max_batches=None, host_entry=False):
+CHAIN_KNOBS = ("ABEA_CHAIN_CAP_DIV", "ABEA_CHAIN_SLOTS", "ABEA_CHAIN_CHUNK_SAMPLES", "ABEA_CHAIN_CHUNK_READS", "ABEA_CHAIN_TABLE_FORMAT",
+               "ABEA_CHAIN_TABLE_COPY")
+
+
+def run(*args, **kw):
+    """_run, with the ABEA_CHAIN_* settings the host-entry mode draws put back as they were afterwards: left in the process's
+    environment they would steer whatever runs next in it (a later test then gets whole 24-byte tables where it expects the default)"""
+    saved = {key: os.environ.get(key) for key in CHAIN_KNOBS}
+    try:
+        return _run(*args, **kw)
+    finally:
+        for key, val in saved.items():
+            if val is None:
+                os.environ.pop(key, None)
+            else:
+                os.environ[key] = val
+
+
+def _run(budget=60.0, seed=1, ctx=None, max_batches=None, host_entry=False):
     """Fuzz for `budget` seconds (or max_batches); returns (batches, signals, events, seconds).  Raises on any mismatch.
     host_entry: the same signals as FLOAT ADC counts through abea_events_batch_host — the chunk pipeline of abea_chain.cpp — with
     random chunk sizes, slot counts, first-guess table capacities (n/1 .. n/64 + 16 events: overflowing tables take the redo path) and both
